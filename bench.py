@@ -24,6 +24,14 @@ Usage (driver contract):
   torchrun --nproc-per-node N bench.py --gpus N --steps K --warmup W
 
 Rank 0 prints exactly ONE JSON line with the aggregate result.
+
+A plain run sets up, warms up, times the K waves and prints that line.
+`--dump-outputs DIR` also writes what the last timed wave returned to its
+caller (per-pod Allocate results, see OUTPUT_FIELDS) as DIR/<name>.npy; pod
+names and sizes are a pure function of the arguments, so two builds can be
+compared output for output.  `--full` adds what the headline figure does not
+need: with real devices, the daemon's deep health probe (gfx950 MFMA + VRAM
+canary kernels) on every benchmarked GPU, run in a child process.
 """
 
 from __future__ import annotations
@@ -31,6 +39,7 @@ from __future__ import annotations
 import argparse
 import json
 import os
+import shutil
 import subprocess
 import sys
 import tempfile
@@ -48,6 +57,7 @@ from gpushare_amd.cluster.podmanager import PodManager
 from gpushare_amd.deviceplugin.stubkubelet import DevicePluginClient
 from gpushare_amd.deviceplugin.server import GPUSharePlugin
 from gpushare_amd.extender.server import ExtenderClient
+from tests.helpers import short_tmp_base
 
 NODE = "bench-node"
 
@@ -74,6 +84,20 @@ def parse_args():
         default=None,
         help="force mock device source, e.g. 8x288GiB (default: real GPUs, "
         "mock fallback when none present)",
+    )
+    p.add_argument(
+        "--dump-outputs",
+        metavar="DIR",
+        default=None,
+        help="after the timed steps, write what the last timed wave's "
+        "Allocate calls returned (one row per pod, ranks concatenated) as "
+        "DIR/<name>.npy float64 arrays",
+    )
+    p.add_argument(
+        "--full",
+        action="store_true",
+        help="also run what the headline figure does not need: with real "
+        "devices, the gfx950 canary health probe in a child process",
     )
     return p.parse_args()
 
@@ -119,6 +143,56 @@ def make_pod_spec(name: str, mem: int) -> dict:
 
 MIXED_SIZES = [8, 16, 32, 64, 128]
 
+# --dump-outputs columns: one value per pod of the last timed wave
+OUTPUT_FIELDS = (
+    "requested_units",      # the pod's gpu-mem limit (the wave's input)
+    "bound",                # 1 = the extender bound the pod
+    "gpu_index",            # ALIYUN_COM_GPU_MEM_IDX; -1 = refused or unbound
+    "units_by_pod",         # ALIYUN_COM_GPU_MEM_POD
+    "units_by_container",   # ALIYUN_COM_GPU_MEM_CONTAINER
+    "units_by_dev",         # ALIYUN_COM_GPU_MEM_DEV
+    "visible_device_count", # entries in HIP_VISIBLE_DEVICES (0 when poisoned)
+    "memguard_limit_bytes", # GPUSHARE_MEM_LIMIT_BYTES; -1 = not injected
+    "device_spec_count",    # /dev nodes injected
+    "mount_count",          # mounts injected
+)
+
+
+def output_row(mem: int, c) -> list[float]:
+    """OUTPUT_FIELDS for one pod; `c` is its ContainerAllocateResponse, or
+    None when the extender refused to bind it."""
+    if c is None:
+        return [float(mem), 0.0, -1.0, 0.0, 0.0, 0.0, 0.0, -1.0, 0.0, 0.0]
+    envs = c.envs
+    ok = envs[consts.ENV_RESOURCE_INDEX] != "-1"
+    return [
+        float(mem),
+        1.0,
+        float(envs[consts.ENV_RESOURCE_INDEX]),
+        float(envs[consts.ENV_RESOURCE_BY_POD]),
+        float(envs[consts.ENV_RESOURCE_BY_CONTAINER]),
+        float(envs[consts.ENV_RESOURCE_BY_DEV]),
+        float(len(envs[consts.ENV_HIP_VISIBLE].split(","))) if ok else 0.0,
+        float(envs.get(consts.ENV_MEMGUARD_LIMIT, "-1")),
+        float(len(c.devices)),
+        float(len(c.mounts)),
+    ]
+
+
+def dump_outputs(outdir: str, rows: list, wave: list) -> None:
+    """Write the last timed wave's results as float64 .npy files: one
+    <field>.npy per OUTPUT_FIELDS column (ranks concatenated in rank order,
+    pods in submission order) plus wave_summary.npy = [allocated, failed,
+    peak packing %] summed / maxed over ranks."""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    table = np.asarray(rows, dtype=np.float64).reshape(-1, len(OUTPUT_FIELDS))
+    for col, name in enumerate(OUTPUT_FIELDS):
+        np.save(os.path.join(outdir, f"{name}.npy"), table[:, col].copy())
+    np.save(os.path.join(outdir, "wave_summary.npy"),
+            np.asarray(wave, dtype=np.float64))
+
 
 class RateLimiter:
     """Paces one rank's pod submissions at rate/world pods/s."""
@@ -146,8 +220,12 @@ def run_wave(
     grains: list[str],
     rate_limiter=None,
     barrier=None,
+    record=None,
 ) -> tuple[int, int, float]:
-    """One churn wave for this rank.  Returns (allocated, failed, peak_packing)."""
+    """One churn wave for this rank.  Returns (allocated, failed, peak_packing).
+
+    `record`, when a list, receives one OUTPUT_FIELDS row per pod: what the
+    wave's caller got back from the extender and from Allocate."""
     n_pods = args.pods_per_gpu
     pods = []
     # deterministic "random" mixed sizes (no global RNG: reproducible per rank/step)
@@ -175,11 +253,15 @@ def run_wave(
         if err:
             failed += 1
             api.delete_pod("default", name)
+            if record is not None:
+                record.append(output_row(mem, None))
             continue
         t0 = time.perf_counter()
         resp = plugin_client.allocate([grains[:mem]])
         lat_allocate.append(time.perf_counter() - t0)
         envs = resp.container_responses[0].envs
+        if record is not None:
+            record.append(output_row(mem, resp.container_responses[0]))
         if envs[consts.ENV_RESOURCE_INDEX] == "-1":
             failed += 1
         else:
@@ -217,6 +299,20 @@ def main():
         # apiserver and extender run as their own processes (as in a real
         # cluster) so the plugin's GIL is not shared with them.
         gpus, source_kind = get_gpus(args.gpus, args.mock)
+        if args.full and source_kind == "amdsmi":
+            # the daemon's deep health probe (gfx950 MFMA + VRAM canary
+            # kernels) in a disposable child, as the daemon runs it, so the
+            # HIP runtime never enters this process
+            from gpushare_amd.health import probe_in_subprocess
+
+            for g in gpus:
+                probe = probe_in_subprocess(g.index, 64)
+                if not probe["ok"]:
+                    raise RuntimeError(
+                        f"canary probe failed on GPU {g.index}: {probe}")
+                print(f"# canary GPU {g.index}: ok "
+                      f"(mfma {probe['mfma_launch_ms']:.3f} ms)",
+                      file=sys.stderr)
         repo = os.path.dirname(os.path.abspath(__file__))
         api_proc = subprocess.Popen(
             [sys.executable, "-m", "gpushare_amd.cluster.fakeapiserver",
@@ -259,7 +355,8 @@ def main():
             apiserver_retries=0,
             informer=informer,
         )
-        sockdir = tempfile.mkdtemp(prefix="gpushare-bench-")
+        # unix socket paths hold at most 107 characters: not under a deep $TMPDIR
+        sockdir = tempfile.mkdtemp(prefix="gpushare-bench-", dir=short_tmp_base())
         plugin = GPUSharePlugin(
             gpus, Allocator(gpus, pm), socket_dir=sockdir
         )
@@ -312,13 +409,19 @@ def main():
     t0 = time.perf_counter()
     allocated = failed = 0
     packing_samples = []
+    last_rows: list = []   # --dump-outputs: the last timed wave's results
+    last_wave = [0, 0, 0.0]
     for step in range(args.steps):
         if distributed:
             dist.barrier()  # align waves: capacity invariant needs all ranks'
                             # deletes from wave N-1 done before wave N creates
+        keep = args.dump_outputs and step == args.steps - 1
         a, f, peak = run_wave(rank, step, api, ext, plugin_client, args,
                               lat_allocate, lat_extender, grains, limiter,
-                              dist.barrier if distributed else None)
+                              dist.barrier if distributed else None,
+                              last_rows if keep else None)
+        if keep:
+            last_wave = [a, f, peak]
         allocated += a
         failed += f
         packing_samples.append(peak)
@@ -354,6 +457,8 @@ def main():
                 "lat_allocate": lat_allocate,
                 "lat_extender": lat_extender,
                 "packing": packing_samples,
+                "last_rows": last_rows,
+                "last_wave": last_wave,
             },
             gathered,
             dst=0,
@@ -367,6 +472,8 @@ def main():
                 "lat_allocate": lat_allocate,
                 "lat_extender": lat_extender,
                 "packing": packing_samples,
+                "last_rows": last_rows,
+                "last_wave": last_wave,
             }
         ]
 
@@ -380,6 +487,14 @@ def main():
         packing_peak = max(
             (p for g in gathered for p in g["packing"]), default=0.0
         )
+        if args.dump_outputs:
+            dump_outputs(
+                args.dump_outputs,
+                [row for g in gathered for row in g["last_rows"]],
+                [sum(g["last_wave"][0] for g in gathered),
+                 sum(g["last_wave"][1] for g in gathered),
+                 max(g["last_wave"][2] for g in gathered)],
+            )
         import resource
 
         server_stats = plugin.allocator.stats.snapshot()
@@ -443,11 +558,14 @@ def main():
     if rank == 0:
         informer.stop()
         plugin.stop()
+        shutil.rmtree(sockdir, ignore_errors=True)
         ext_proc.terminate()
         api_proc.terminate()
         ext_proc.wait(timeout=5)
         api_proc.wait(timeout=5)
-    os._exit(0)
+    # leave through the interpreter's normal exit so atexit hooks and
+    # library finalizers (profilers, tracers) run; only daemon threads
+    # remain, and the watchdog above still covers a wedged shutdown
 
 
 if __name__ == "__main__":

@@ -3,11 +3,22 @@
 from __future__ import annotations
 
 import itertools
+import os
+import tempfile
 import time
 
 from gpushare_amd import consts
 
 _counter = itertools.count()
+
+
+def short_tmp_base() -> str:
+    """A writable temp root short enough to parent a unix socket (sun_path
+    holds at most 107 characters, which a deep $TMPDIR can use up)."""
+    for base in (tempfile.gettempdir(), "/tmp", "/dev/shm", "/var/tmp"):
+        if len(base) <= 60 and os.path.isdir(base) and os.access(base, os.W_OK):
+            return base
+    return tempfile.gettempdir()
 
 
 def make_pod(

@@ -40,7 +40,7 @@ def api():
     server.stop()
 
 
-def test_daemon_main_with_kubeconfig(api, tmp_path):
+def test_daemon_main_with_kubeconfig(api, tmp_path, tmp_socket_dir):
     kubeconfig = tmp_path / "kubeconfig"
     kubeconfig.write_text(
         json.dumps(  # valid YAML (JSON subset)
@@ -57,9 +57,8 @@ def test_daemon_main_with_kubeconfig(api, tmp_path):
             }
         )
     )
-    sockdir = tmp_path / "dp"
-    sockdir.mkdir()
-    kubelet = StubKubelet(str(sockdir))
+    sockdir = tmp_socket_dir
+    kubelet = StubKubelet(sockdir)
     kubelet.start()
     env = dict(os.environ)
     env.update(
@@ -69,7 +68,7 @@ def test_daemon_main_with_kubeconfig(api, tmp_path):
     )
     proc = subprocess.Popen(
         [sys.executable, "-m", "gpushare_amd.cli.daemon",
-         "--mock-spec", "2x16GiB", "--socket-dir", str(sockdir)],
+         "--mock-spec", "2x16GiB", "--socket-dir", sockdir],
         env=env, cwd=REPO,
         stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
     )
@@ -93,7 +92,7 @@ def test_daemon_main_with_kubeconfig(api, tmp_path):
             proc.wait(timeout=10)
         kubelet.stop()
     # socket unlinked on graceful stop
-    assert not os.path.exists(sockdir / consts.SERVER_SOCK_NAME)
+    assert not os.path.exists(os.path.join(sockdir, consts.SERVER_SOCK_NAME))
 
 
 def test_selftest_cli_passes():

@@ -92,7 +92,7 @@ def test_ecc_counters_readable(smi):
     assert uncorr == 0, f"GPU reports uncorrectable ECC errors: {uncorr}"
 
 
-def test_e2e_allocate_and_tenant_workloads(source, tmp_path):
+def test_e2e_allocate_and_tenant_workloads(source, tmp_socket_dir):
     """Full plugin round on real hardware, then two *concurrent* tenant
     processes sharing GPU 0 under the allocation's envs — the actual
     gpushare co-location semantics."""
@@ -105,8 +105,7 @@ def test_e2e_allocate_and_tenant_workloads(source, tmp_path):
     from helpers import make_pod
 
     gpus = source.devices()
-    sockdir = str(tmp_path / "dp")
-    os.makedirs(sockdir)
+    sockdir = tmp_socket_dir
     kube = FakeKubeClient(node_name="gpu-node")
     pm = PodManager(kube, "gpu-node", kubelet_client=kube.as_kubelet(), cache_ttl=0.0)
     plugin = GPUSharePlugin(gpus, Allocator(gpus, pm), socket_dir=sockdir)
@@ -165,7 +164,7 @@ def test_e2e_allocate_and_tenant_workloads(source, tmp_path):
         kubelet.stop()
 
 
-def test_allocate_envs_drive_memguard_end_to_end(source, tmp_path):
+def test_allocate_envs_drive_memguard_end_to_end(source, tmp_socket_dir):
     """The FULL enforcement chain on a real MI355X: a pod's Allocate
     response (not hand-crafted envs) configures the tenant — LD_PRELOAD
     mount + budget + pod/container scoping all come from the plugin, and
@@ -186,8 +185,7 @@ def test_allocate_envs_drive_memguard_end_to_end(source, tmp_path):
     assert os.path.exists(lib), "memguard not built"
 
     gpus = source.devices()
-    sockdir = str(tmp_path / "dp")
-    os.makedirs(sockdir)
+    sockdir = tmp_socket_dir
     kube = FakeKubeClient(node_name="gpu-node")
     pm = PodManager(
         kube, "gpu-node", kubelet_client=kube.as_kubelet(), cache_ttl=0.0
@@ -260,7 +258,7 @@ def test_allocate_envs_drive_memguard_end_to_end(source, tmp_path):
         kubelet.stop()
 
 
-def test_manager_e2e_on_gpu(source, tmp_path):
+def test_manager_e2e_on_gpu(source, tmp_socket_dir):
     """Full lifecycle manager with the real device source on an MI355X."""
     import threading
 
@@ -269,7 +267,7 @@ def test_manager_e2e_on_gpu(source, tmp_path):
     from gpushare_amd.deviceplugin.stubkubelet import StubKubelet
     from gpushare_amd.lifecycle import ManagerOptions, SharedGPUManager
 
-    sockdir = str(tmp_path / "dp")
+    sockdir = tmp_socket_dir
     kube = FakeKubeClient(node_name="gpu-node")
     mgr = SharedGPUManager(
         source, kube, "gpu-node",
