@@ -74,6 +74,12 @@ class HealthMonitor:
         event_recorder=None,
         probe_mode: str = "subprocess",     # "subprocess" | "inproc"
     ):
+        if deep_probe_interval > 0 and probe_vram_mb < 1:
+            # _canary.probe refuses such a span each interval, which would
+            # mark every GPU Unhealthy at run time; fail at start-up instead
+            raise ValueError(
+                f"probe_vram_mb must be at least 1, got {probe_vram_mb}"
+            )
         self.source = source
         self.plugin = plugin
         self.deep_probe_interval = deep_probe_interval

@@ -79,6 +79,7 @@ def test_canary_probe_mfma_and_vram():
     result = canary.probe(0, vram_probe_mb=128, bandwidth=True)
     assert result["mfma_ok"], f"MFMA canary mismatch: {result}"
     assert result["vram_ok"], f"VRAM pattern mismatch: {result}"
+    assert result["hbm_copy_mismatches"] == 0, result
     assert "gfx950" in result["arch"], result["arch"]
     # HBM3E streaming copy should comfortably exceed 1 TB/s
     assert result["hbm_copy_gbps"] > 1000, result
