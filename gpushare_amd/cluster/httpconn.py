@@ -1,4 +1,4 @@
-"""Persistent keep-alive HTTP session on stdlib ``http.client``.
+"""Persistent keep-alive HTTP session; native round trips where built.
 
 The control-plane hot path (Allocate → pending-pod LIST + ASSIGNED PATCH,
 extender filter/bind) is 4–6 small localhost/apiserver REST round-trips per
@@ -12,14 +12,25 @@ reference's Allocate p50 too (client-go against the same apiserver,
 SURVEY §3.2), so cutting it is a genuine like-for-like win, not a
 benchmark trick.
 
-Thread safety: ``http.client`` connections are not thread-safe; each thread
-gets its own connection via ``threading.local``.  Stale keep-alive sockets
-(peer restarted, idle timeout) are retried once on a fresh connection.
+Thread safety: connections are not thread-safe; each thread gets its own
+connection via ``threading.local``.  Stale keep-alive sockets (peer
+restarted, idle timeout) are retried once on a fresh connection.
+
+Transport: with the ``gpushare_amd._httprt`` extension importable, request
+assembly, the socket exchange and response parsing run in C++ with the GIL
+released (``native/http_rt.cpp``); for ``https://`` the socket stays an
+``ssl.SSLSocket`` and only assembly and parsing are native.  Without the
+extension, or with ``GPUSHARE_HTTP_NATIVE=0`` in the environment when the
+session is made, everything goes through stdlib ``http.client`` as before.
+Both transports put the same bytes on the wire and raise the same
+exceptions.
 """
 
 from __future__ import annotations
 
 import http.client
+import importlib
+import os
 import socket
 import ssl
 import threading
@@ -83,6 +94,67 @@ def make_ssl_context(verify) -> Optional[ssl.SSLContext]:
     return ssl.create_default_context()
 
 
+def _load_native():
+    """The ``_httprt`` extension module, or None where it is not built."""
+    try:
+        return importlib.import_module("gpushare_amd._httprt")
+    except ImportError:
+        return None
+
+
+class _TlsConn:
+    """One TLS connection with ``_httprt.Conn``'s interface: the handshake
+    and the record layer stay in ``ssl`` (so verification and ``SSLError``
+    behave as with ``HTTPSConnection``), head assembly and response parsing
+    are the native ones."""
+
+    def __init__(self, rt, host, port, timeout, ctx):
+        self._rt = rt
+        self._host_hdr = rt.host_header(host, port, 443)
+        self.keep_alive = False
+        sock = socket.create_connection((host, port), timeout)
+        try:
+            sock.setsockopt(socket.IPPROTO_TCP, socket.TCP_NODELAY, 1)
+            self._sock = ctx.wrap_socket(sock, server_hostname=host)
+        except BaseException:
+            sock.close()
+            raise
+        self._parser = rt.ResponseParser()
+        self._buf = bytearray(65536)
+
+    def roundtrip(self, method, path, headers, body):
+        head = self._rt.build_head(
+            method, path, self._host_hdr, headers,
+            None if body is None else len(body),
+        )
+        parser, sock, buf = self._parser, self._sock, self._buf
+        parser.reset(method.upper() == "HEAD")
+        self.keep_alive = False
+        sock.sendall(head + body if body else head)
+        view = memoryview(buf)
+        got = False
+        while True:
+            n = sock.recv_into(buf)
+            if n == 0:
+                if not got:
+                    raise http.client.RemoteDisconnected(
+                        "Remote end closed connection without response"
+                    )
+                parser.finish_eof()
+                break
+            got = True
+            if parser.feed(view[:n]):
+                break
+        status, data, self.keep_alive = parser.result()
+        return status, data
+
+    def close(self):
+        try:
+            self._sock.close()
+        except OSError:
+            pass
+
+
 class HttpSession:
     """Keep-alive HTTP/1.1 client bound to one base URL."""
 
@@ -105,6 +177,13 @@ class HttpSession:
         self._headers = dict(headers or {})
         self._local = threading.local()
         self._closed = False
+        # read here, not at import: one process can hold sessions of both
+        # kinds (parity tests, before/after measurements)
+        self._rt = (
+            None
+            if os.environ.get("GPUSHARE_HTTP_NATIVE", "1") == "0"
+            else _load_native()
+        )
 
     # ------------------------------------------------------------------ #
     def _connect(self) -> http.client.HTTPConnection:
@@ -118,6 +197,57 @@ class HttpSession:
             )
         self._local.conn = conn
         return conn
+
+    def _connect_native(self):
+        if self._https:
+            conn = _TlsConn(
+                self._rt, self._host, self._port, self._timeout, self._ctx
+            )
+        else:
+            conn = self._rt.Conn(self._host, self._port, self._timeout)
+        self._local.conn = conn
+        return conn
+
+    def _request_native(self, method, full, body, hdrs) -> tuple[int, bytes]:
+        local = self._local
+        conn = getattr(local, "conn", None)
+        fresh = conn is None
+        if fresh:
+            conn = self._connect_native()
+        for attempt in (0, 1):
+            try:
+                result = conn.roundtrip(method, full, hdrs, body)
+                if not conn.keep_alive:
+                    # the server will close (or has closed) its end: the
+                    # next request starts on a new connection
+                    conn.close()
+                    local.conn = None
+                return result
+            except ValueError:
+                # refused before a byte was written (CR/LF in a header,
+                # non-ASCII path): the connection is untouched
+                raise
+            except (
+                http.client.RemoteDisconnected,
+                http.client.BadStatusLine,
+                BrokenPipeError,
+                ConnectionResetError,
+                ConnectionRefusedError,
+                ssl.SSLEOFError,
+            ):
+                conn.close()
+                local.conn = None
+                if fresh or attempt == 1:
+                    raise
+                conn = self._connect_native()
+                fresh = True
+            except BaseException:
+                # a timeout above all: the request reached a live-but-slow
+                # server, retrying could double-apply a non-idempotent verb.
+                # Whatever it was, this connection's framing is lost.
+                conn.close()
+                local.conn = None
+                raise
 
     def request(
         self,
@@ -135,6 +265,8 @@ class HttpSession:
             raise RuntimeError("session closed")
         hdrs = self._headers if headers is None else {**self._headers, **headers}
         full = self._prefix + path
+        if self._rt is not None:
+            return self._request_native(method, full, body, hdrs)
         conn = getattr(self._local, "conn", None)
         fresh = conn is None
         if fresh:
@@ -177,7 +309,18 @@ class HttpSession:
         """Open a long-lived streaming request (k8s watch) on a DEDICATED
         connection — never the pooled one, which must stay request/response.
         Caller reads the response incrementally and closes the returned
-        connection."""
+        connection.
+
+        Over plain http with the native transport both returned objects are
+        one ``_httprt.LineStream`` (``status``, ``readline()``, ``read()``,
+        ``close()``), whose reader waits with the GIL released."""
+        hdrs = self._headers if headers is None else {**self._headers, **headers}
+        if self._rt is not None and not self._https:
+            ls = self._rt.LineStream(
+                self._host, self._port, timeout, self._prefix + path, hdrs,
+                method,
+            )
+            return ls, ls
         if self._https:
             conn = http.client.HTTPSConnection(
                 self._host, self._port, timeout=timeout, context=self._ctx
@@ -186,7 +329,6 @@ class HttpSession:
             conn = http.client.HTTPConnection(
                 self._host, self._port, timeout=timeout
             )
-        hdrs = self._headers if headers is None else {**self._headers, **headers}
         try:
             conn.request(method, self._prefix + path, headers=hdrs)
             resp = conn.getresponse()

@@ -1,11 +1,12 @@
 """In-tree build of the native extensions (no JIT cache, no network).
 
-Builds three extensions next to the package so the .so files travel with a
+Builds four extensions next to the package so the .so files travel with a
 repo snapshot:
 
   gpushare_amd._amdsmi  — C++  dlopen shim over libamd_smi.so   (g++)
   gpushare_amd._devlist — C++  ListAndWatchResponse pre-encoder (g++)
   gpushare_amd._canary  — HIP  gfx950 health-probe kernels      (hipcc)
+  gpushare_amd._httprt  — C++  keep-alive HTTP/1.1 round trips  (g++)
   libgpushare_memguard.so — C++ LD_PRELOAD VRAM budget enforcer (g++;
                             plain shared lib, not a Python extension)
 
@@ -39,10 +40,10 @@ _COMMON = [
 ]
 
 
-def _needs_build(src: Path, out: Path, force: bool) -> bool:
+def _needs_build(srcs: list[Path], out: Path, force: bool) -> bool:
     if force or not out.exists():
         return True
-    return src.stat().st_mtime > out.stat().st_mtime
+    return any(s.stat().st_mtime > out.stat().st_mtime for s in srcs)
 
 
 def _run(cmd: list[str]) -> None:
@@ -61,6 +62,7 @@ def build(force: bool = False, verbose: bool = True) -> list[Path]:
             [f"-I{ROCM}/include", "-ldl"],
         ),
         ("g++", HERE / "devlist_codec.cpp", PKG / f"_devlist{EXT_SUFFIX}", []),
+        ("g++", HERE / "http_rt.cpp", PKG / f"_httprt{EXT_SUFFIX}", []),
         (
             os.path.join(ROCM, "bin", "hipcc"),
             HERE / "canary.hip",
@@ -76,8 +78,10 @@ def build(force: bool = False, verbose: bool = True) -> list[Path]:
             ["-fvisibility=default", "-ldl"],
         ),
     ]
+    # headers a target includes from this directory
+    deps = {"http_rt.cpp": [HERE / "http_parse.h"]}
     for compiler, src, out, extra in targets:
-        if not _needs_build(src, out, force):
+        if not _needs_build([src, *deps.get(src.name, [])], out, force):
             continue
         _run([compiler, *_COMMON, str(src), "-o", str(out), *extra])
         built.append(out)
@@ -92,11 +96,15 @@ def main() -> None:
     sys.path.insert(0, str(PKG.parent))
     import gpushare_amd._amdsmi as smi  # noqa: F401
     import gpushare_amd._devlist as dl  # noqa: F401
+    import gpushare_amd._httprt as rt
 
     print("[native/build] _amdsmi available:", smi.available())
     c = dl.DeviceListCodec(["amd-0-_-0"])
     assert len(c.encode()) > 0
     print("[native/build] _devlist OK")
+    head = rt.build_head("GET", "/", "localhost", {"Accept": "*/*"})
+    assert head.startswith(b"GET / HTTP/1.1\r\nHost: localhost\r\n")
+    print("[native/build] _httprt OK")
 
 
 if __name__ == "__main__":
